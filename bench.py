@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """bench.py -- Mpix/s remapped on the BASELINE.json workload, with roofline, verification and CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|3|1|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--config 2|3|1|4] [--full] [--dump-outputs DIR]
+
+A plain run does what the headline needs and nothing else: set-up, warm-up (the first step, untimed steps while the
+clocks ramp, then the W warm-up steps), ONE timed region of exactly K steps, and the JSON line.  `--full` adds every
+other leg described below: R = 5 repeats of the timed region (the median is reported), the pipelined, strong-scaling and
+8-GPU projection legs, the oracle verification and per-frame checksums, the native C++ driver, the host-pointer ABI, the
+HBM copy rate and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed -- its output planes, what a caller of the path receives --
+as float32 .npy files under DIR (a fixed, seeded sample of whole frames and of pixels across the step, <= 64 MB in all),
+so that two builds can be compared output for output: the inputs are the same seeded frames in every run.
 
 With --gpus N > 1 and no launcher environment the script starts its N ranks itself (it re-executes under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one rank per GPU);
@@ -13,9 +22,9 @@ counter-hash noise generated on the device and RESIDENT IN HBM before the timed 
 pass of the hot path (all three planes, ONE fused kernel launch) over one batch of F frames (default 64: 708 MB of
 input, far larger than the 256 MB Infinity Cache).
 
-Timing: W warm-up steps, then R = 5 repeats of EXACTLY K steps, each repeat bracketed by a barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over the ranks; the MEDIAN repeat is reported (box-to-box
-and run-to-run spread on the pool is a few percent).  With the driver's K = 20 that is 6 400 frames per rank.
+Timing: W warm-up steps, then EXACTLY K steps bracketed by a barrier + torch.cuda.synchronize() on both sides and
+reduced with MAX over the ranks; with --full R = 5 such repeats and the MEDIAN repeat is reported (box-to-box and
+run-to-run spread on the pool is a few percent).  With K = 20 that is 1 280 frames per rank (6 400 with --full).
 
 Multi-GPU: whole frames are sharded across ranks, no data-path collective.  With N > 1 ranks the HEADLINE (`value`,
 `ms_per_step`, `roofline`, "scaling": "strong") is BASELINE.json configs[4] as written: 64 frames per step IN TOTAL,
@@ -29,7 +38,7 @@ ceil(64/N) per rank, so a 1-2-4-8 GPU series of this line is the strong-scaling 
 Everything a rank does is run_rank(); `--stub` runs that same function with a CPU stand-in for the transform under
 gloo (tests/test_host_cpu.py: the code the 8-GPU run executes is the code the CPU test covers).
 
-Extra records of the default line (one GPU, config 2): "strong_cfg5.projected_8_gpus" = what one GPU of an 8-GPU node runs for
+Extra records of the --full line (one GPU, config 2): "strong_cfg5.projected_8_gpus" = what one GPU of an 8-GPU node runs for
 configs[4] (8 frames per step) timed on this GPU, and "two_streams" = the same steps alternating between two handles on two
 HIP streams (independent batches; the tail of one launch overlaps the start of the next).  Neither enters `value`;
 --no-two-streams leaves the overlapped launches out (kernel traces).
@@ -622,6 +631,40 @@ def traffic_record(lib_path, kernel_name, frames, config):
             os.path.relpath(path, ROOT), sha, tr["hbm_read_bytes_per_launch"], tr["hbm_write_bytes_per_launch"])
 
 
+DUMP_FRAME_BYTES = 48 << 20   # --dump-outputs: float32 bytes of whole output frames, all ranks together
+DUMP_SAMPLES = 1 << 20         # --dump-outputs: output bytes sampled across the whole step, all ranks together (12 B each)
+
+
+def dump_outputs(out_dir, path, lout, n_frames, rank, world):
+    """--dump-outputs: what the last timed step handed its caller -- the output planes of its n_frames frames on this rank
+    -- as float32 .npy files in out_dir: y / u / v = (k, h, w) planes of k whole frames (`frames` = their index in the
+    step) and `sample` = the output byte at each of `sample_offset` (offsets into the step's output buffer: every frame,
+    every plane).  Frames and offsets come from a fixed seed and the input frames are seeded, so two runs with the same
+    arguments dump the same positions of the same work.  With N > 1 ranks every name carries `_rank<r>`."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = path.d_out[:n_frames * lout.frame_bytes].cpu().numpy()
+    rng = np.random.default_rng(0x360)
+    tag = "" if world == 1 else "_rank%d" % rank
+    arrays = {}
+
+    def save(name, a):
+        np.save(os.path.join(out_dir, name + tag + ".npy"), a)
+        arrays[name + tag] = list(a.shape)
+
+    k = min(n_frames, DUMP_FRAME_BYTES // world // (4 * lout.payload_bytes()))
+    if k:
+        frames = np.sort(rng.choice(n_frames, k, replace=False))
+        save("frames", frames.astype(np.float64))
+        for p, name in enumerate("yuv"):
+            save(name, np.stack([lout.plane_view(host[j * lout.frame_bytes:(j + 1) * lout.frame_bytes], p)
+                                 for j in frames]).astype(np.float32))
+    off = np.sort(rng.integers(0, host.size, min(host.size, DUMP_SAMPLES // world)))
+    save("sample_offset", off.astype(np.float64))
+    save("sample", host[off].astype(np.float32))
+    return {"dir": out_dir, "arrays": arrays}
+
+
 def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
     """Everything one rank does; returns the record on rank 0 (None elsewhere).  `Path` is HipPath (the benchmark) or
     StubPath (the CPU rehearsal of this very function under gloo)."""
@@ -645,8 +688,9 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
 
     busy = {"s": 0.0}   # wall-clock seconds this rank kept the GPU busy with transform steps (timed or not)
 
-    def timed_run(n_frames, steps, with_events, after_step=None, rotate=False, before_step=None, alternate=False, pipelined=False):
-        """REPEATS x (exactly `steps` steps between barriers); per repeat (elapsed max over ranks, [launch ms]).
+    def timed_run(n_frames, steps, with_events, after_step=None, rotate=False, before_step=None, alternate=False, pipelined=False,
+                  repeats=REPEATS):
+        """`repeats` x (exactly `steps` steps between barriers); per repeat (elapsed max over ranks, [launch ms]).
         rotate: step k reads the k-th group of n_frames input frames of this rank's F (a short step must not find its
         input in the 256 MB Infinity Cache just because every step reads the same few frames)."""
         ring_frames = getattr(path, "groups", 1) * F
@@ -656,7 +700,7 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
         fast = None
         if after_step is None and before_step is None and not alternate and hasattr(path, "fast_steps"):
             fast = path.fast_steps(n_frames, steps, groups if ring is not None else 1, pipelined)
-        for _ in range(REPEATS):
+        for _ in range(repeats):
             # ONE event pair around the K launches of the timed region (on the stream the kernels run on): the average
             # launch duration is its span / K, gaps between launches included.  A pair per step cost 7 us per step -- 3 %
             # of a 64-frame step that is measurement, not work.
@@ -734,16 +778,32 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
         path.sync()
         clock_warmup_steps += 8
     busy["s"] += time.perf_counter() - t_w
-    warm_steps(F, args.warmup)
-    runs = timed_run(F, args.steps, True, rotate=rotate)
-    if getattr(path, "groups", 1) > 1:
-        path.step(F)  # d_out holds group 0's result again
-        path.sync()
-    elapsed, launch_ms = sorted(runs, key=lambda r: r[0])[len(runs) // 2]
-    kernel_name = path.kernel_name()
+
+    # Which leg is the headline.  One GPU: K steps of F frames (BASELINE configs[1]; with F = 64 also configs[4] at N = 1).
+    # N > 1 GPUs on the default workload: BASELINE configs[4] AS WRITTEN -- 64 frames per step IN TOTAL, ceil(64 / N) per
+    # rank, strong scaling -- so that a 1-2-4-8 GPU series of this line is the strong-scaling curve of configs[4] and not
+    # eight independent copies of the one-GPU job.  The weak figure (F frames per GPU) stays
+    # in the --full line as `weak_value` / "weak_64_frames_per_gpu".  A plain run times the headline leg only, once.
+    full = args.full
+    repeats = REPEATS if full else 1
+    f5 = min(F, -(-64 // world))
+    headline_strong = world > 1 and args.config == 2 and F == 64
+    dumped = None
+
+    runs = elapsed = launch_ms = kernel_name = None
+    if full or not headline_strong:
+        warm_steps(F, args.warmup)
+        runs = timed_run(F, args.steps, True, rotate=rotate, repeats=repeats)
+        if args.dump_outputs and not headline_strong:
+            dumped = dump_outputs(args.dump_outputs, path, lout, F, rank, world)
+        if full and getattr(path, "groups", 1) > 1:
+            path.step(F)  # d_out holds group 0's result again
+            path.sync()
+        elapsed, launch_ms = sorted(runs, key=lambda r: r[0])[len(runs) // 2]
+        kernel_name = path.kernel_name()
 
     pipelined = None
-    if path.name == "hip" and not args.no_two_streams:
+    if full and path.name == "hip" and not args.no_two_streams:
         path.set_pipeline(args.pipeline_depth)
         for k in range(2 * args.pipeline_depth):
             path.k = k
@@ -765,24 +825,25 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
     # BASELINE configs[4] as written: 64 frames in total, frame-sharded -> ceil(64 / N) per rank (strong scaling).  No
     # events inside: a step of 8 frames is 40 us and two event records per step are 10 % of it.
     strong = None
-    f5 = min(F, -(-64 // world))
-    if args.config == 2:
+    if args.config == 2 and (full or headline_strong):
         warm_steps(f5, max(2, args.warmup))
         # with N > 1 ranks this leg IS the headline (`value`, `roofline`): one event pair around its K launches then
-        sruns = timed_run(f5, args.steps, world > 1, rotate=rotate)
+        sruns = timed_run(f5, args.steps, world > 1, rotate=rotate, repeats=repeats)
+        if args.dump_outputs and headline_strong:
+            dumped = dump_outputs(args.dump_outputs, path, lout, f5, rank, world)
         s_el, s_launch_ms = sorted(sruns, key=lambda r: r[0])[len(sruns) // 2]
         strong_kernel = path.kernel_name()
         strong = {"frames_total": 64, "frames_per_gpu": f5, "n_gpus": world, "scaling": "strong",
                   "ms_per_step": round(s_el / args.steps * 1e3, 4),
                   "value": round(min(64, f5 * world) * args.steps / s_el * out_w * out_h / 1e6, 1), "unit": "Mpix/s",
                   "repeats_ms_per_step": [round(r[0] / args.steps * 1e3, 4) for r in sruns]}
-        if rotate and getattr(path, "groups", 1) * F > f5:
+        if full and rotate and getattr(path, "groups", 1) * F > f5:
             # the same f5 input frames every step (88 MB for 8 frames: they stay in the 256 MB Infinity Cache)
             cruns = timed_run(f5, args.steps, False, rotate=False)
             c_el = sorted(r[0] for r in cruns)[len(cruns) // 2]
             strong["input"] = "every step reads other frames of the rank's %d-frame ring (HBM)" % (getattr(path, "groups", 1) * F)
             strong["ms_per_step_same_input_every_step"] = round(c_el / args.steps * 1e3, 4)
-        if path.name == "hip" and not args.no_two_streams:
+        if full and path.name == "hip" and not args.no_two_streams:
             # The same steps through T360_transformFramesPipelined (ONE handle, the library's internal streams): a frame
             # stream's consecutive batches are independent, so step k+1's workgroups start while step k's last ones drain
             # (the overlap is a product feature now, not two handles in the benchmark).
@@ -797,7 +858,7 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
                                            "independent batches, %d output buffers" % (args.pipeline_depth, args.pipeline_depth),
                                    "ms_per_step": round(p_el / args.steps * 1e3, 4),
                                    "value": round(min(64, f5 * world) * args.steps / p_el * out_w * out_h / 1e6, 1), "unit": "Mpix/s"}
-        if world == 1 and F >= 64 and path.name == "hip":
+        if full and world == 1 and F >= 64 and path.name == "hip":
             # what ONE GPU of an 8-GPU node runs for configs[4]: 8 of the 64 frames per step.  Timed here on one GPU (input
             # rotating through the ring, so from HBM): the projected strong-scaling factor is t(64 frames) / t(8 frames).
             t_w8 = time.perf_counter()
@@ -907,7 +968,7 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
                     "compute_only_ms_per_step": round(elapsed / args.steps * 1e3, 4)}
         path.step(F)  # d_out holds a full-batch result again
         path.sync()
-    elif strong is not None:
+    elif full and strong is not None:
         path.step(F)  # d_out holds a full-batch result again for the verification below
         path.sync()
 
@@ -976,8 +1037,8 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
         path.sync()
 
     # verification outside the timed region: oracle comparison of frames of the last step + the checksum of every frame
-    verified = None
-    if not args.no_verify:
+    verified = checksums = None
+    if full and not args.no_verify:
         frames = sorted({0, min(15, F - 1), min(16, F - 1), min(31, F - 1), min(32, F - 1), F - 1})
         if args.config == 4:
             frames = frames[:2]  # 12.6 Mpix Lanczos4 frames: seconds each on the host
@@ -986,9 +1047,10 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
         if dist is not None:
             dist.all_reduce(ok, op=dist.ReduceOp.MIN)
         verified["all_ranks_ok"] = bool(int(ok.item()))
-    sums = path.frame_sums(F)
-    all_sums = sharding.gather_checksums({rank * F + j: v for j, v in enumerate(sums)}, F * world, dist, coll_dev)
-    checksums = [sum(all_sums[r * F:(r + 1) * F]) for r in range(world)]
+    if full:
+        sums = path.frame_sums(F)
+        all_sums = sharding.gather_checksums({rank * F + j: v for j, v in enumerate(sums)}, F * world, dist, coll_dev)
+        checksums = [sum(all_sums[r * F:(r + 1) * F]) for r in range(world)]
 
     res = None
     if rank == 0:
@@ -997,13 +1059,8 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
             raise SystemExit(1)
         out_mpix = out_w * out_h / 1e6
         alg_frame = lin.payload_bytes() + lout.payload_bytes()
-        weak_fps = args.steps * F * world / elapsed
-        # Which leg is the headline.  One GPU: K steps of F frames (BASELINE configs[1]; with F = 64 also configs[4] at N = 1).
-        # N > 1 GPUs on the default workload: BASELINE configs[4] AS WRITTEN -- 64 frames per step IN TOTAL, ceil(64 / N) per
-        # rank, strong scaling -- so that a 1-2-4-8 GPU series of this line is the strong-scaling curve of configs[4] and not
-        # eight independent copies of the one-GPU job.  The weak figure (F frames per GPU) stays
-        # in the line as `weak_value` / "weak_64_frames_per_gpu".
-        headline_strong = world > 1 and strong is not None and F == 64
+        weak_fps = args.steps * F * world / elapsed if elapsed is not None else None
+        # the headline leg (`headline_strong`: see where the timed legs start)
         if headline_strong:
             h_elapsed, h_frames_step, h_launch_ms, h_kernel, h_F = s_el, min(64, f5 * world), s_launch_ms, strong_kernel, f5
         else:
@@ -1026,7 +1083,7 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
             # per step in total, plain calls; == `value` when N > 1), `weak_value` = F frames per GPU and step (== `value` at N = 1)
             "strong_cfg5_value": strong["value"] if strong is not None else None,
             "strong_cfg5_pipelined_value": (strong.get("pipelined") or {}).get("value") if strong is not None else None,
-            "weak_value": round(weak_fps * out_mpix, 1),
+            "weak_value": round(weak_fps * out_mpix, 1) if weak_fps is not None else None,
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(h_elapsed / args.steps * 1e3, 4),
             "higher_is_better": True,
@@ -1044,13 +1101,13 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
             "first_step_ms": round(first_step_ms, 1), "cold_ms_per_step_steps_2_to_9": round(cold_ms_per_step, 4),
             "clock_warmup_steps": clock_warmup_steps,
             "library_sha16": lib_sha,
-            "repeats": REPEATS, "repeats_ms_per_step": [round(r[0] / args.steps * 1e3, 4) for r in (sruns if headline_strong else runs)],
+            "repeats": repeats, "repeats_ms_per_step": [round(r[0] / args.steps * 1e3, 4) for r in (sruns if headline_strong else runs)],
             "input_ring": {"groups_of_F_frames": getattr(path, "groups", 1), "bytes": getattr(path, "groups", 1) * F * lin.frame_bytes,
                            "why": "timed steps rotate through this much distinct input, several times the 256 MB Infinity Cache: a step "
                                   "whose input fits the cache would find it there, and even re-reading ONE 708 MB batch of config 2 every "
                                   "step measured 1 % faster than rotating through three (0.2370 vs 0.2395 ms, round 5, "
                                   "profiles/r05_experiments/README.md call 5; rounds 1-4 did the former)"},
-            "frames_timed_per_gpu": REPEATS * args.steps * h_F,
+            "frames_timed_per_gpu": repeats * args.steps * h_F,
             # context for the timed region: `ms_per_step` x steps is a few milliseconds; over the
             # whole run this rank kept the GPU busy with transform steps (clock ramp, warm-up, every timed leg) for
             "gpu_busy_s_all_legs": round(busy["s"], 3),
@@ -1072,7 +1129,7 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
         }
         if strong is not None:
             res["strong_cfg5"] = strong
-        if headline_strong:
+        if headline_strong and runs is not None:
             res["weak_64_frames_per_gpu"] = {"value": round(weak_fps * out_mpix, 1), "unit": "Mpix/s", "scaling": "weak",
                                              "ms_per_step": round(elapsed / args.steps * 1e3, 4), "frames_per_step_per_gpu": F,
                                              "kernel": kernel_name,
@@ -1085,6 +1142,8 @@ def run_rank(args, Path, dist, rank, world, coll_dev, wl, ctx):
             res["gather_outputs"] = gathered
         if scattered is not None:
             res["scatter_gather"] = scattered
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
     return res, path, (lin, lout)
 
 
@@ -1113,7 +1172,14 @@ def main():
                     help="config 3: T360_setFusedLowpass(1) -- the low-pass inside the gather tiles (off by default: slower, DESIGN.md 5.2)")
     ap.add_argument("--stub", action="store_true",
                     help="CPU rehearsal of the rank function with a stand-in transform (tests; never a benchmark result)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg besides the headline: repeats, pipelined / strong-scaling / 8-GPU projection legs, "
+                         "oracle verification and checksums, native driver, host-pointer ABI, HBM copy rate, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (a seeded sample of its output planes, float32 .npy) to DIR")
     args = ap.parse_args()
+    if not args.full and (args.gather_outputs or args.scatter_inputs or args.two_handles):
+        ap.error("--gather-outputs, --scatter-inputs and --two-handles are legs of the --full run")
     if args.fused_lowpass:
         os.environ["T360_BENCH_FUSED_LOWPASS"] = "1"
 
@@ -1176,7 +1242,7 @@ def main():
     # rank 0 runs the native driver over all `world` devices while the other ranks wait on the rendezvous store (a CPU-side
     # wait: an RCCL barrier would park a spinning kernel on every other GPU).
     native = None
-    if not args.stub and args.config == 2 and not args.no_native and not build_flags:
+    if args.full and not args.stub and args.config == 2 and not args.no_native and not build_flags:
         path.sync()
         store = None
         if dist is not None:
@@ -1202,7 +1268,7 @@ def main():
         if not args.stub:
             res["library"] = {"path": os.path.relpath(_lib.LIB_PATH, ROOT), "build_flags": build_flags,
                               "version": _lib.load().T360_version().decode()}
-        if world == 1 and not args.stub:
+        if args.full and world == 1 and not args.stub:
             # "achievable" HBM rate of this box for reference: a plain device-to-device copy (read + write)
             try:
                 n = 1 << 30
@@ -1220,9 +1286,9 @@ def main():
             except RuntimeError:
                 pass
         res["Mpix_s_in"] = round(res["fps"] * wl["in_w"] * wl["in_h"] / 1e6, 1)
-        if world == 1 and args.config == 2 and not args.no_host_abi and not args.stub:
+        if args.full and world == 1 and args.config == 2 and not args.no_host_abi and not args.stub:
             res["host_abi"] = host_abi_rate(wl, lin, lout, ctx)
-        if not args.no_cpu_baseline and world == 1 and not args.stub:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.stub:
             res["cpu_baseline"] = cpu_baseline(wl, lin, lout, args.cpu_seconds)
         print(json.dumps(res))
     path.close()

@@ -258,7 +258,7 @@ def test_bench_rank_function_world_size_2_gloo():
     out = subprocess.check_output(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
          "--master-port", "29741", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--frames", "6", "--steps", "3",
-         "--warmup", "1", "--gather-outputs", "--scatter-inputs"], env=env, stderr=subprocess.DEVNULL, timeout=300, cwd=ROOT).decode()
+         "--warmup", "1", "--full", "--gather-outputs", "--scatter-inputs"], env=env, stderr=subprocess.DEVNULL, timeout=300, cwd=ROOT).decode()
     rec = json.loads([line for line in out.splitlines() if line.startswith("{")][-1])
     assert rec["n_gpus"] == 2 and rec["steps"] == 3 and rec["scaling"] == "weak"
     assert rec["metric"].startswith("STUB")               # a rehearsal can never be mistaken for a result
@@ -282,7 +282,7 @@ def test_bench_headline_is_strong_scaling_with_two_ranks():
     out = subprocess.check_output(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
          "--master-port", "29743", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub", "--steps", "2",
-         "--warmup", "1"], env=env, stderr=subprocess.DEVNULL, timeout=300, cwd=ROOT).decode()
+         "--warmup", "1", "--full"], env=env, stderr=subprocess.DEVNULL, timeout=300, cwd=ROOT).decode()
     rec = json.loads([line for line in out.splitlines() if line.startswith("{")][-1])
     assert rec["n_gpus"] == 2 and rec["scaling"] == "strong"
     assert rec["config"]["frames_per_step_total"] == 64 and rec["config"]["frames_per_step_per_gpu"] == 32
@@ -290,6 +290,33 @@ def test_bench_headline_is_strong_scaling_with_two_ranks():
     assert rec["value"] == s["value"] == rec["strong_cfg5_value"] and rec["ms_per_step"] == s["ms_per_step"]
     assert w["scaling"] == "weak" and w["frames_per_step_per_gpu"] == 64 and rec["weak_value"] == w["value"]
     assert rec["roofline"]["algorithmic_bytes_per_launch"] > 0 and rec["roofline"]["avg_launch_ms"] > 0
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """A plain bench.py run (no --full) times exactly --steps steps once and runs no other leg; --dump-outputs writes the
+    output of the LAST timed step (here step 1 of 2, which read the second batch of the input ring), float32, <= 64 MB,
+    the same in two runs with the same arguments."""
+    import json
+    recs = []
+    for run in ("a", "b"):
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--stub", "--frames", "8", "--steps", "2",
+                                       "--warmup", "1", "--dump-outputs", str(tmp_path / run)],
+                                      stderr=subprocess.DEVNULL, timeout=300, cwd=ROOT).decode()
+        recs.append(json.loads([line for line in out.splitlines() if line.startswith("{")][-1]))
+    rec = recs[0]
+    assert rec["steps"] == 2 and rec["repeats"] == 1 and rec["frames_timed_per_gpu"] == 2 * 8 and rec["ms_per_step"] > 0
+    assert rec["verified"] is None and rec["output_checksums"] is None and "strong_cfg5" not in rec and "cpu_baseline" not in rec
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == ["frames.npy", "sample.npy", "sample_offset.npy", "u.npy", "v.npy", "y.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 * 10 ** 6
+    d = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    for n in names:
+        assert np.array_equal(d[n[:-4]], np.load(tmp_path / "b" / n)) and d[n[:-4]].dtype in (np.float32, np.float64)
+    lin, lout = FrameLayout(256, 128), FrameLayout(96, 64)     # the stub's frames; out = 255 - the first bytes of in
+    want = np.concatenate([255 - noise_bytes(lin.frame_bytes, frame_seed(1_000_000 + j))[:lout.frame_bytes] for j in range(8, 16)])
+    assert np.array_equal(d["sample"], want[d["sample_offset"].astype(np.int64)].astype(np.float32))
+    for i, j in enumerate(d["frames"].astype(int)):
+        assert np.array_equal(d["y"][i], lout.plane_view(want[j * lout.frame_bytes:(j + 1) * lout.frame_bytes], 0))
 
 
 def test_native_multi_gpu_driver_bookkeeping(tmp_path):

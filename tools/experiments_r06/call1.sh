@@ -8,7 +8,7 @@ cd $R
 echo "== smem_stream"; timeout 120 tools/ubench/smem_stream.bin 2>&1 | tee $O/smem_stream.txt
 for CFG in 3 2; do
 for FR in 64 32 16 8; do
-  timeout 300 python bench.py --config $CFG --frames $FR --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native > $O/out.json 2> $O/err.txt
+  timeout 300 python bench.py --full --config $CFG --frames $FR --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native > $O/out.json 2> $O/err.txt
   python - <<PY
 import json
 try:

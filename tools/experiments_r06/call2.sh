@@ -5,7 +5,7 @@ O=$R/gpurun_out/r06_call2; mkdir -p $O
 cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; grep -a -E "passed|failed|error" $O/pytest.log | tail -3
 for CFG in 3 2; do
-  timeout 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native > $O/out$CFG.json 2> $O/err$CFG.txt
+  timeout 300 python bench.py --full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native > $O/out$CFG.json 2> $O/err$CFG.txt
   python - <<PY
 import json
 try:

@@ -5,7 +5,7 @@ R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/r06_call5; mkdir -p $O
 cd $R
 python tools/dev/fused_debug.py 2>&1 | grep "frame 0\|frame 24" | grep -v " 0 of " | head
-B="python bench.py --config 3 --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native"
+B="python bench.py --full --config 3 --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native"
 timeout 300 $B > $O/ship.json 2> $O/ship.err; python - <<PY
 import json
 d = json.loads(open("$O/ship.json").read().strip().splitlines()[-1]); print("shipped lib: ms/step", d.get("ms_per_step"), "pipelined", (d.get("pipelined") or {}).get("ms_per_step"), "verified", (d.get("verified") or {}).get("max_abs_diff"), d.get("error"))

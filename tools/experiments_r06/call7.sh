@@ -6,7 +6,7 @@ cd $R
 timeout 1500 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; grep -a -E "passed|failed|error" $O/pytest.log | tail -3
 for REP in 1 2; do
 for ARG in "" "--fused-lowpass"; do
-  timeout 300 python bench.py --config 3 --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native $ARG > $O/out.json 2> $O/err.txt
+  timeout 300 python bench.py --full --config 3 --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native $ARG > $O/out.json 2> $O/err.txt
   python - <<PY
 import json
 try:

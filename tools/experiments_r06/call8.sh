@@ -4,7 +4,7 @@
 R=$(cd "$(dirname "$0")/../.." && pwd)
 O=$R/gpurun_out/r06_call8; mkdir -p $O
 cd $R
-B="python bench.py --config 4 --steps 6 --warmup 2 --no-cpu-baseline --no-host-abi --no-native --no-two-streams"
+B="python bench.py --full --config 4 --steps 6 --warmup 2 --no-cpu-baseline --no-host-abi --no-native --no-two-streams"
 run() { # label env...
   local label=$1; shift
   env "$@" timeout 600 $B > $O/out.json 2> $O/err.txt

@@ -9,7 +9,7 @@ export T360_LIB=$R/transform360_amd/lib/libTransform360_instr.so T360_BENCH_ALLO
 for CFG in 2 3; do
 for PAD in 0 12000; do
 for DEPTH in 2 3; do
-  T360_LDS_PAD=$PAD timeout 300 python bench.py --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native --pipeline-depth $DEPTH > $O/out.json 2> $O/err.txt
+  T360_LDS_PAD=$PAD timeout 300 python bench.py --full --config $CFG --steps 20 --warmup 3 --no-cpu-baseline --no-host-abi --no-native --pipeline-depth $DEPTH > $O/out.json 2> $O/err.txt
   python - <<PY
 import json
 try:
