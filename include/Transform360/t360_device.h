@@ -91,6 +91,37 @@ int T360_transformFramesPipelinedMany(VideoFrameTransform* transform, int n_call
 int T360_setPipelineDepth(VideoFrameTransform* transform, int depth);
 int T360_pipelineJoin(VideoFrameTransform* transform);
 
+/* ---- per-frame view orientation ---- */
+
+/* Degrees; the meaning of FrameTransformContext.fixed_yaw / fixed_pitch / fixed_roll
+ * (reference VideoFrameTransform.cpp:1233-1246, and :1266-1268 for FLAT_FIXED, which ignores roll). */
+typedef struct T360Pose { float yaw, pitch, roll; } T360Pose;
+
+/* As T360_transformFrames, but output frame k is what the reference produces for input frame k with
+ * a handle whose context equals this one's except fixed_yaw/pitch/roll = poses[k].
+ * in_frame_bytes == 0 is allowed: every output then reads input frame 0 (N views of one frame).
+ * poses[] is read before the call returns; the caller may reuse it at once.  Asynchronous on the handle's stream.
+ *   - VideoFrameTransform_generateMapForPlane must have been called for every map index used: it fixes the dimensions,
+ *     the interpolation tables, the low-pass segments and the libm tables.  The handle's own maps, sample LUTs and gather
+ *     plans are not touched: T360_copyMap and later T360_transformFrames calls return what they did before.
+ *   - Ordered like T360_transformFrames: on the handle's stream, after what is queued there (pipelined lanes are not
+ *     waited for; T360_pipelineJoin first if a pipelined call's output is this call's input).  No host synchronisation,
+ *     no device allocation once the low-pass scratch of the batch size exists; capturable.
+ *   - The low-pass (adjust_kernel == 0: its kernels do not depend on the pose) runs once per input frame before the
+ *     gather, once in all when in_frame_bytes == 0.
+ * Refused (0, a message, no output byte written): poses == NULL, n_frames <= 0, a non-finite angle, a plane whose output
+ * size differs from its map's, width_scale_factor or height_scale_factor != 1, enable_low_pass_filter with adjust_kernel
+ * (the reference's segment kernels then depend on yaw and pitch, VideoFrameTransform.cpp:263-291). */
+int T360_transformFramesPosed(VideoFrameTransform* transform,
+                              const uint8_t* d_in, int64_t in_frame_bytes,
+                              uint8_t* d_out, int64_t out_frame_bytes,
+                              int n_frames, const T360PlaneDesc* planes, int n_planes,
+                              const T360Pose* poses);
+
+/* The warp map (2*w*h floats, as T360_copyMap) that map_index would have for *pose.  It is computed by the
+ * SAME device projection code the posed gather runs.  For parity tests.  Synchronous. */
+int T360_copyPosedMap(VideoFrameTransform* transform, int map_index, const T360Pose* pose, float* host_dst);
+
 /* Low-pass contexts, batches of >= 24 frames, bilinear / bicubic, MONO input: on = 1 makes the gather tiles whose source rows
  * all have fixed-point kernels of <= 7 horizontal and 3 vertical taps filter their own footprint in LDS (ONE pass over the raw
  * plane: reference filterPlane feeding remap, VideoFrameTransform.cpp:727-733 + :748-754, without the blurred plane's round

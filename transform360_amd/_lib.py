@@ -26,6 +26,7 @@ ADDITIVE_SYMBOLS = (
     "T360_filterPlane", "T360_getMapSize", "T360_copyMap", "T360_getSegmentCount", "T360_getSegment",
     "T360_copySegmentKernels", "T360_fillNoise", "T360_lastKernel", "T360_lastLowpassPath", "T360_getPlanStats", "T360_buildFlags",
     "T360_transformFramesPipelined", "T360_transformFramesPipelinedMany", "T360_setPipelineDepth", "T360_pipelineJoin", "T360_setFusedLowpass",
+    "T360_transformFramesPosed", "T360_copyPosedMap",
 )
 
 
@@ -38,6 +39,11 @@ class T360PlaneDesc(C.Structure):
         ("out_width", C.c_int), ("out_height", C.c_int),
         ("map_index", C.c_int),
     ]
+
+
+class T360Pose(C.Structure):
+    """include/Transform360/t360_device.h: T360Pose (degrees, the meaning of fixed_yaw / fixed_pitch / fixed_roll)."""
+    _fields_ = [("yaw", C.c_float), ("pitch", C.c_float), ("roll", C.c_float)]
 
 
 def build(verbose=False):
@@ -88,6 +94,9 @@ def load():
     L.T360_transformFramesPipelined.argtypes = [vp, u8p, C.c_int64, u8p, C.c_int64, i, C.POINTER(T360PlaneDesc), i]
     L.T360_transformFramesPipelinedMany.argtypes = [vp, i, C.POINTER(C.c_void_p), C.c_int64, C.POINTER(C.c_void_p), C.c_int64, i,
                                                     C.POINTER(T360PlaneDesc), i]
+    L.T360_transformFramesPosed.argtypes = [vp, u8p, C.c_int64, u8p, C.c_int64, i, C.POINTER(T360PlaneDesc), i,
+                                            C.POINTER(T360Pose)]
+    L.T360_copyPosedMap.argtypes = [vp, i, C.POINTER(T360Pose), vp]
     L.T360_setPipelineDepth.argtypes = [vp, i]
     L.T360_setFusedLowpass.argtypes = [vp, i]
     L.T360_pipelineJoin.argtypes = [vp]

@@ -132,6 +132,20 @@ T360_EXPORT int T360_transformFramesPipelinedMany(VideoFrameTransform* t, int n_
   });
 }
 
+T360_EXPORT int T360_transformFramesPosed(VideoFrameTransform* t, const uint8_t* d_in, int64_t in_frame_bytes,
+                                          uint8_t* d_out, int64_t out_frame_bytes, int n_frames,
+                                          const T360PlaneDesc* planes, int n_planes, const T360Pose* poses) {
+  if (!t) return 0;
+  return guarded("T360_transformFramesPosed", [&] {
+    return t->transformFramesPosed(d_in, in_frame_bytes, d_out, out_frame_bytes, n_frames, planes, n_planes, poses);
+  });
+}
+
+T360_EXPORT int T360_copyPosedMap(VideoFrameTransform* t, int map_index, const T360Pose* pose, float* host_dst) {
+  if (!t) return 0;
+  return guarded("T360_copyPosedMap", [&] { return t->copyPosedMap(map_index, pose, host_dst); });
+}
+
 T360_EXPORT int T360_setFusedLowpass(VideoFrameTransform* t, int on) {
   if (!t) return 0;
   return guarded("T360_setFusedLowpass", [&] { return t->setFusedLowpass(on != 0); });

@@ -12,6 +12,37 @@ namespace t360 {
 hipError_t launch_mapgen(const MapGenParams& P, float2* map, LutEntry* lut, hipStream_t stream);
 hipError_t launch_fill_noise(uint8_t* dst, int64_t nbytes, uint64_t seed, hipStream_t stream);
 
+// ---- posed gather (t360_posed.hip): projection + quantisation + gather in one pass, one pose per frame ----
+// Per-frame pose constants travel in the kernel arguments (no device buffer, no host copy): a launch covers up to
+// kPosedChunk frames.  Planes are flattened onto grid.x (64x16-px tiles), frames of the chunk go on grid.y.
+constexpr int kPosedChunk = 64;
+constexpr int kPosedTileW = 64, kPosedTileH = 16;  // workgroup 16 x 16 lanes, 4 horizontally adjacent pixels per lane
+constexpr int kPosedMaxPlanes = 4;
+struct PosePod {
+  float rot[9];            // pose_rotation() coefficients
+  float yaw_deg, pitch_deg;  // FLAT_FIXED
+};
+struct PosedPlane {
+  MapGenParams gen;        // the map's projection constants (rot / yaw_deg / pitch_deg unused: the pose replaces them)
+  const uint8_t* src;      // plane base of the chunk's first frame
+  int64_t src_frame_bytes;  // 0: every frame reads the same source
+  uint8_t* dst;
+  int64_t dst_frame_bytes;
+  int sw, sh, sstride;
+  int dstride;             // the output plane is gen.map_w x gen.map_h
+  int tile0, tiles_x;      // first grid.x index of this plane, tiles per tile row
+};
+struct PosedArgs {
+  const int16_t* wtab;
+  int nplanes;
+  int dst_dword_ok;        // every plane's base, stride and frame distance are 4-byte aligned
+  PosedPlane plane[kPosedMaxPlanes];
+  PosePod pose[kPosedChunk];
+};
+// grid.x = tiles of all planes, grid.y = frames of the chunk (<= kPosedChunk); kernel name for T360_lastKernel
+hipError_t launch_remap_posed(const PosedArgs& a, int nframes, int total_tiles, int interp, bool transparent, hipStream_t stream);
+const char* remap_posed_kernel_name(int interp);
+
 // ---- gather (t360_remap.hip) ----
 // One plane of `nframes` frames: frame f lives at src + f*src_frame_bytes / dst + f*dst_frame_bytes.
 struct GatherArgs {

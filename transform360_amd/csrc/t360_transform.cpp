@@ -387,6 +387,26 @@ bool VideoFrameTransform::ensureWeights() {
   return true;
 }
 
+void t360::pose_rotation(float yaw_deg, float pitch_deg, float roll_deg, float rot[9]) {
+  // :1233-1244 -- double sin/cos of (deg * M_PI / 180.0f) narrowed to float, then the float
+  // coefficient expressions in the reference's association order
+  const float s1 = (float)std::sin(yaw_deg * M_PI / 180.0f);
+  const float s2 = (float)std::sin(pitch_deg * M_PI / 180.0f);
+  const float s3 = (float)std::sin(roll_deg * M_PI / 180.0f);
+  const float c1 = (float)std::cos(yaw_deg * M_PI / 180.0f);
+  const float c2 = (float)std::cos(pitch_deg * M_PI / 180.0f);
+  const float c3 = (float)std::cos(roll_deg * M_PI / 180.0f);
+  rot[0] = c1 * c3 + s1 * s2 * s3;
+  rot[1] = c3 * s1 * s2 - c1 * s3;
+  rot[2] = c2 * s1;
+  rot[3] = c2 * s3;
+  rot[4] = c2 * c3;
+  rot[5] = -s2;
+  rot[6] = c1 * s2 * s3 - c3 * s1;
+  rot[7] = c1 * c3 * s2 + s1 * s3;
+  rot[8] = c1 * c2;
+}
+
 // reference VideoFrameTransform::generateMapForPlane (VideoFrameTransform.cpp:504-576)
 bool VideoFrameTransform::generateMapForPlane(int inputWidth, int inputHeight, int outputWidth,
                                               int outputHeight, int idx) {
@@ -462,25 +482,7 @@ bool VideoFrameTransform::generateMapForPlane(int inputWidth, int inputHeight, i
   P.pitch_deg = ctx_.fixed_pitch;
   P.input_pixel_width = 1.0f / inputWidth;  // :528-531
   if (ctx_.input_stereo_format == STEREO_FORMAT_LR) P.input_pixel_width *= 2;
-  {
-    // :1233-1244 -- double sin/cos of (deg * M_PI / 180.0f) narrowed to float, then the float
-    // coefficient expressions in the reference's association order
-    const float s1 = (float)std::sin(ctx_.fixed_yaw * M_PI / 180.0f);
-    const float s2 = (float)std::sin(ctx_.fixed_pitch * M_PI / 180.0f);
-    const float s3 = (float)std::sin(ctx_.fixed_roll * M_PI / 180.0f);
-    const float c1 = (float)std::cos(ctx_.fixed_yaw * M_PI / 180.0f);
-    const float c2 = (float)std::cos(ctx_.fixed_pitch * M_PI / 180.0f);
-    const float c3 = (float)std::cos(ctx_.fixed_roll * M_PI / 180.0f);
-    P.rot[0] = c1 * c3 + s1 * s2 * s3;
-    P.rot[1] = c3 * s1 * s2 - c1 * s3;
-    P.rot[2] = c2 * s1;
-    P.rot[3] = c2 * s3;
-    P.rot[4] = c2 * c3;
-    P.rot[5] = -s2;
-    P.rot[6] = c1 * s2 * s3 - c3 * s1;
-    P.rot[7] = c1 * c3 * s2 + s1 * s3;
-    P.rot[8] = c1 * c2;
-  }
+  pose_rotation(ctx_.fixed_yaw, ctx_.fixed_pitch, ctx_.fixed_roll, P.rot);
 
   // Column / row tables of the layouts whose per-pixel libm calls depend on one coordinate only
   // (t360_internal.h, MapGenParams::col_tab).  The front end below is transformPos :903-938 for
@@ -671,6 +673,7 @@ bool VideoFrameTransform::generateMapForPlane(int inputWidth, int inputHeight, i
   // host vectors above go out of scope: finish the uploads (init-time only)
   if (!check(hipStreamSynchronize(stream_), "hipStreamSynchronize")) return false;
   if (!buildResizePlan(p, p.out_w, p.out_h)) return false;
+  p.gen = P;
   p.valid = true;
   return true;
 }
@@ -1639,6 +1642,159 @@ bool VideoFrameTransform::transformFrames(const uint8_t* d_in, int64_t in_frame_
                             d.map_index, k});
   }
   return runPlanes(jobs.data(), (int)jobs.size(), n_frames);
+}
+
+// T360_transformFramesPosed: low-pass (pose-independent contexts only) into the scratch planes, then the posed gather,
+// which evaluates the projection per pixel for its frame's pose (t360_posed.hip).  Nothing of the handle's per-map state
+// is written; the pose coefficients are computed here and passed by value in the launch arguments.
+bool VideoFrameTransform::transformFramesPosed(const uint8_t* d_in, int64_t in_frame_bytes, uint8_t* d_out,
+                                               int64_t out_frame_bytes, int n_frames, const T360PlaneDesc* planes,
+                                               int n_planes, const T360Pose* poses) {
+  if (!ok_) return false;
+  const char* what = "transform360: T360_transformFramesPosed";
+  if (!d_in || !d_out || !planes || n_planes <= 0 || !poses || n_frames <= 0 || in_frame_bytes < 0 || out_frame_bytes < 0) {
+    printf("%s: invalid arguments\n", what);
+    return false;
+  }
+  for (int k = 0; k < n_frames; k++)
+    if (!std::isfinite(poses[k].yaw) || !std::isfinite(poses[k].pitch) || !std::isfinite(poses[k].roll)) {
+      printf("%s: pose %d is not finite\n", what, k);
+      return false;
+    }
+  if (ctx_.width_scale_factor != 1.0f || ctx_.height_scale_factor != 1.0f) {
+    printf("%s: width_scale_factor and height_scale_factor must be 1\n", what);
+    return false;
+  }
+  if (ctx_.enable_low_pass_filter && ctx_.adjust_kernel) {
+    printf("%s: the low-pass with adjust_kernel depends on the pose (not supported)\n", what);
+    return false;
+  }
+  const int interp = (int)ctx_.interpolation_alg;
+  if (!valid_interp(interp)) {
+    printf("%s: unknown interpolation algorithm\n", what);
+    return false;
+  }
+  std::vector<PlaneJob> jobs;
+  for (int k = 0; k < n_planes; k++) {
+    const T360PlaneDesc& d = planes[k];
+    if (d.map_index < 0 || d.map_index >= kMaxMaps || !planes_[d.map_index].valid) {
+      printf("Could not transform the plane %d. Error: no map generated for index %d\n", k, d.map_index);
+      return false;
+    }
+    const PlaneState& p = planes_[d.map_index];
+    if (d.in_width <= 0 || d.in_height <= 0 || d.in_stride < d.in_width || d.out_stride < d.out_width) {
+      printf("Could not transform the plane %d. Error: invalid plane description\n", k);
+      return false;
+    }
+    if (d.out_width != p.map_w || d.out_height != p.map_h) {
+      printf("%s: plane %d: output %dx%d differs from its map's %dx%d (no resize in posed calls)\n", what, k, d.out_width,
+             d.out_height, p.map_w, p.map_h);
+      return false;
+    }
+    jobs.push_back(PlaneJob{d_in + d.in_offset, in_frame_bytes, d.in_width, d.in_height, d.in_stride,
+                            d_out + d.out_offset, out_frame_bytes, d.out_width, d.out_height, d.out_stride,
+                            d.map_index, k});
+  }
+  DeviceGuard g(device_);
+  const int n_src = in_frame_bytes == 0 ? 1 : n_frames;  // frames that really are distinct inputs
+  struct Src {
+    const uint8_t* ptr;
+    int64_t frame_bytes;
+    int stride;
+  };
+  std::vector<Src> srcs((size_t)n_planes);
+  if (ctx_.enable_low_pass_filter) {
+    // the stand-alone low-pass of every plane into the call's scratch (runPlanes stage 1, per plane, never fused)
+    std::vector<size_t> offs((size_t)n_planes);
+    size_t total = 0;
+    for (int k = 0; k < n_planes; k++) {
+      offs[(size_t)k] = total;
+      total += (size_t)((jobs[(size_t)k].in_w + 255) & ~255) * jobs[(size_t)k].in_h * (size_t)n_src;
+    }
+    if (!blurred_[scratch_].reserve(total)) return check(hipErrorOutOfMemory, "hipMalloc(blurred)");
+    for (int k = 0; k < n_planes; k++) {
+      const PlaneJob& j = jobs[(size_t)k];
+      const int bstride = (j.in_w + 255) & ~255;
+      const int64_t plane_bytes = (int64_t)bstride * j.in_h;
+      uint8_t* bl = blurred_[scratch_].as<uint8_t>() + offs[(size_t)k];
+      PlaneState& p = planes_[j.idx];
+      if (!runLowpass(p, p.lp, nullptr, j.in, j.in_frame_bytes, j.in_stride, bl, plane_bytes, bstride, j.in_w, j.in_h, n_src,
+                      j.image_plane, stream_))
+        return false;
+      srcs[(size_t)k] = Src{bl, in_frame_bytes == 0 ? 0 : plane_bytes, bstride};
+    }
+    last_lowpass_ = "per-plane";
+  } else {
+    for (int k = 0; k < n_planes; k++) srcs[(size_t)k] = Src{jobs[(size_t)k].in, in_frame_bytes, jobs[(size_t)k].in_stride};
+  }
+  const bool barrel = ctx_.output_layout == LAYOUT_BARREL || ctx_.output_layout == LAYOUT_BARREL_SPLIT;
+  bool dword_ok = true;
+  for (const PlaneJob& j : jobs) {
+    // :743-747 -- chroma of the barrel layouts starts as 128, then BORDER_TRANSPARENT leaves the unmapped pixels
+    if (barrel && j.idx != 0 &&
+        !check(launch_fill_plane(j.out, j.out_frame_bytes, j.out_w, j.out_h, j.out_stride, 128, n_frames, stream_), "fill launch"))
+      return false;
+    dword_ok = dword_ok && (reinterpret_cast<uintptr_t>(j.out) & 3) == 0 && (j.out_stride & 3) == 0 &&
+               (n_frames <= 1 || (j.out_frame_bytes & 3) == 0);
+  }
+  // launches: up to kPosedMaxPlanes planes x kPosedChunk frames each
+  PosedArgs a;
+  for (int g0 = 0; g0 < n_planes; g0 += kPosedMaxPlanes) {
+    memset(&a, 0, sizeof(a));
+    a.wtab = weights_.as<int16_t>();
+    a.dst_dword_ok = dword_ok ? 1 : 0;
+    int tiles = 0;
+    for (int k = g0; k < n_planes && a.nplanes < kPosedMaxPlanes; k++) {
+      const PlaneJob& j = jobs[(size_t)k];
+      PosedPlane& pp = a.plane[a.nplanes++];
+      pp.gen = planes_[j.idx].gen;
+      pp.sw = j.in_w;
+      pp.sh = j.in_h;
+      pp.sstride = srcs[(size_t)k].stride;
+      pp.src_frame_bytes = srcs[(size_t)k].frame_bytes;
+      pp.dst_frame_bytes = j.out_frame_bytes;
+      pp.dstride = j.out_stride;
+      pp.tiles_x = (j.out_w + kPosedTileW - 1) / kPosedTileW;
+      pp.tile0 = tiles;
+      tiles += pp.tiles_x * ((j.out_h + kPosedTileH - 1) / kPosedTileH);
+    }
+    for (int c0 = 0; c0 < n_frames; c0 += kPosedChunk) {
+      const int nf = std::min(kPosedChunk, n_frames - c0);
+      for (int q = 0; q < a.nplanes; q++) {
+        a.plane[q].src = srcs[(size_t)(g0 + q)].ptr + (size_t)c0 * a.plane[q].src_frame_bytes;
+        a.plane[q].dst = jobs[(size_t)(g0 + q)].out + (size_t)c0 * a.plane[q].dst_frame_bytes;
+      }
+      for (int f = 0; f < nf; f++) {
+        const T360Pose& ps = poses[c0 + f];
+        pose_rotation(ps.yaw, ps.pitch, ps.roll, a.pose[f].rot);
+        a.pose[f].yaw_deg = ps.yaw;
+        a.pose[f].pitch_deg = ps.pitch;
+      }
+      if (!check(launch_remap_posed(a, nf, tiles, interp, barrel, stream_), "posed remap launch")) return false;
+    }
+  }
+  setLastKernel(remap_posed_kernel_name(interp));
+  return true;
+}
+
+bool VideoFrameTransform::copyPosedMap(int idx, const T360Pose* pose, float* host_dst) {
+  if (!ok_ || idx < 0 || idx >= kMaxMaps || !planes_[idx].valid || !pose || !host_dst) return false;
+  if (!std::isfinite(pose->yaw) || !std::isfinite(pose->pitch) || !std::isfinite(pose->roll)) {
+    printf("transform360: T360_copyPosedMap: the pose is not finite\n");
+    return false;
+  }
+  DeviceGuard g(device_);
+  const PlaneState& p = planes_[idx];
+  MapGenParams P = p.gen;
+  pose_rotation(pose->yaw, pose->pitch, pose->roll, P.rot);
+  P.yaw_deg = pose->yaw;
+  P.pitch_deg = pose->pitch;
+  const size_t n = (size_t)p.map_w * p.map_h;
+  DeviceBuffer map, lut;  // introspection only: scratch of its own, the handle's map and LUT stay as they are
+  if (!map.reserve(n * sizeof(float2)) || !lut.reserve(n * sizeof(LutEntry))) return check(hipErrorOutOfMemory, "hipMalloc(map)");
+  return check(launch_mapgen(P, map.as<float2>(), lut.as<LutEntry>(), stream_), "mapgen launch") &&
+         check(hipStreamSynchronize(stream_), "hipStreamSynchronize") &&
+         check(hipMemcpy(host_dst, map.as<void>(), n * sizeof(float2), hipMemcpyDeviceToHost), "hipMemcpy(map)");
 }
 
 bool VideoFrameTransform::filterPlane(const uint8_t* d_in, uint8_t* d_out, int width, int height, int in_stride,

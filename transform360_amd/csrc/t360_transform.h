@@ -24,6 +24,8 @@ namespace t360 {
 
 // OpenCV's fixed-point 2-D interpolation table for LINEAR / CUBIC / LANCZOS4 (host build).
 bool build_inter_table(int interp, std::vector<int16_t>* tab, int* ksize);
+// rotation coefficients of a pose (reference VideoFrameTransform.cpp:1233-1244), MapGenParams::rot / PosePod::rot
+void pose_rotation(float yaw_deg, float pitch_deg, float roll_deg, float rot[9]);
 
 }  // namespace t360
 
@@ -62,6 +64,10 @@ class VideoFrameTransform {
     return true;
   }
   bool pipelineJoin();
+  // one pose per frame (t360_device.h): projection folded into the gather, the handle's maps untouched
+  bool transformFramesPosed(const uint8_t* d_in, int64_t in_frame_bytes, uint8_t* d_out, int64_t out_frame_bytes,
+                            int n_frames, const T360PlaneDesc* planes, int n_planes, const T360Pose* poses);
+  bool copyPosedMap(int idx, const T360Pose* pose, float* host_dst);
   bool filterPlane(const uint8_t* d_in, uint8_t* d_out, int width, int height, int in_stride,
                    int out_stride, int map_index);
   bool getMapSize(int idx, int* w, int* h) const;
@@ -82,6 +88,7 @@ class VideoFrameTransform {
     t360::DeviceBuffer map;                        // float2[map_h][map_w]
     t360::DeviceBuffer lut;                        // LutEntry[map_h][map_w]
     t360::DeviceBuffer col_tab, row_tab;           // per-column / per-row libm values (MapGenParams)
+    t360::MapGenParams gen;                        // the projection constants the map was generated with (posed calls)
     // INTER_AREA shrink map_w x map_h -> out_w x out_h (only when the scale factors are not 1)
     struct ResizePlan {
       bool needed = false, supported = false, linear = false;

@@ -146,6 +146,30 @@ class VideoFrameTransform:
         return bool(self._l.T360_transformFramesPipelinedMany(self._h, n, ins, in_frame_bytes, outs, out_frame_bytes, n_frames,
                                                               descs, len(descs)))
 
+    def transformFramesPosed(self, d_in, in_layout, d_out, out_layout, n_frames, poses, in_frame_bytes=None):
+        """T360_transformFramesPosed: output frame k seen with poses[k] = (yaw, pitch, roll) in degrees instead of the
+        context's fixed_yaw / fixed_pitch / fixed_roll.  d_in / d_out: flat uint8 CUDA tensors (or raw device addresses)
+        holding frames laid out by the two FrameLayouts; in_frame_bytes defaults to in_layout.frame_bytes, 0 makes every
+        output read input frame 0.  poses: (n_frames, 3) array or a list of triples; copied before the call returns."""
+        arr = make_poses(poses)
+        if len(arr) != n_frames:
+            raise ValueError("%d poses for %d frames" % (len(arr), n_frames))
+        ptr = lambda x: x.data_ptr() if hasattr(x, "data_ptr") else int(x)
+        descs = self.plane_descs(in_layout, out_layout)
+        ifb = in_layout.frame_bytes if in_frame_bytes is None else in_frame_bytes
+        return bool(self._l.T360_transformFramesPosed(self._h, ptr(d_in), ifb, ptr(d_out), out_layout.frame_bytes, n_frames,
+                                                      descs, len(descs), arr))
+
+    def posedMap(self, map_index, pose):
+        """The [h, w, 2] float32 warp map `map_index` would have for pose (yaw, pitch, roll) (T360_copyPosedMap)."""
+        w, h = C.c_int(), C.c_int()
+        if not self._l.T360_getMapSize(self._h, map_index, C.byref(w), C.byref(h)):
+            return None
+        m = np.empty((h.value, w.value, 2), np.float32)
+        if not self._l.T360_copyPosedMap(self._h, map_index, C.byref(make_poses([pose])[0]), m.ctypes.data):
+            return None
+        return m
+
     def setFusedLowpass(self, on):
         """before generateMapForPlane: long batches of a low-pass context filter inside the gather tiles (t360_device.h)"""
         return bool(self._l.T360_setFusedLowpass(self._h, 1 if on else 0))
@@ -196,6 +220,15 @@ class VideoFrameTransform:
             self._l.T360_copySegmentKernels(self._h, map_index, i, kx.ctypes.data, ky.ctypes.data)
             out.append((rect[0], rect[1], rect[2], rect[3], kx, ky, bool(fx.value)))
         return out
+
+
+def make_poses(poses):
+    """ctypes T360Pose array from an (n, 3) array or a list of (yaw, pitch, roll) triples (degrees)."""
+    a = np.asarray(poses, dtype=np.float32).reshape(-1, 3)
+    arr = (_lib.T360Pose * len(a))()
+    for k, (y, p, r) in enumerate(a):
+        arr[k] = _lib.T360Pose(float(y), float(p), float(r))
+    return arr
 
 
 # ---- synthetic stream (SURVEY.md 8d): byte i of a buffer = splitmix64(seed + i) >> 56 ----
