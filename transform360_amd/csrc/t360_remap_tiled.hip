@@ -991,6 +991,8 @@ template <int KS, int P, int K>
 __device__ __forceinline__ void fused_waves(const TiledArgs& a, const TiledPlane& pl, const uint32_t* __restrict__ taps,
                                             const TileDesc& t, const TileFetch& tf, const FusedFetch& ff,
                                             const uint8_t* __restrict__ lds, int f0, int f1) {
+  // the frame loop below unrolls exactly 3 steps (T360_FSTEP(0..2)): a 4th slot would skip every 4th frame
+  static_assert(K >= 2 && K <= 3, "fused_waves unrolls 3 frame steps: K must be 2 or 3");
   // (GROUP = 2: two pixels' stencil reads in flight at a time instead of all four -- 16 registers the filter phase's
   // addresses and row window need; the frame's LDS round trips are dominated by the filter's row steps anyway)
   constexpr int WAVES = 8, NPX = 4, GROUP = T360_FUSED_GROUP;

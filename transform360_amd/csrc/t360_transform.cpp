@@ -1204,18 +1204,37 @@ bool VideoFrameTransform::runPlanes(const PlaneJob* jobs, int njobs, int n_frame
     ta.direct_blocks = (ta.total_direct * ta.groups + 7) & ~7;  // a multiple of 8: staged ids keep their XCD
   };
   reset_fused();
-  // The fused low-pass tiles of the call's planes: ONE launch of remap_fused_kernel.  It reads the raw planes only, so it does
-  // not wait for the low-pass launches below: it goes to a side stream first and runs beside them and beside the tiled
-  // kernel's launch for the plan's other tiles (joined at the end of the call).
+  // The fused low-pass tiles of the call's planes: one launch of remap_fused_kernel per group of up to 4 planes (what a
+  // TiledArgs holds).  Every plane whose lpf flag is set MUST be launched here: the tiled launch below leaves its fused
+  // tiles out.  They read the raw planes only, so they do not wait for the low-pass launches below: they go to a side stream
+  // first, one after the other, and run beside them and beside the tiled kernel's launch for the plan's other tiles
+  // (joined at the end of the call).
   bool lpa_launched = false;
   char lpa_name[48] = "";
   {
     FusedArgs lpa;
-    memset(&lpa, 0, sizeof(lpa));
-    lpa.base = fused;
+    const hipStream_t fs = fuse_side_stream_ ? lp_streams_[2] : stream_;
+    auto reset_lpa = [&]() {
+      memset(&lpa, 0, sizeof(lpa));
+      lpa.base = fused;
+    };
+    auto flush_lpa = [&]() -> bool {
+      if (lpa.base.nplanes == 0) return true;
+      finalize_launch(lpa.base);
+      if (!lpa_launched && fuse_side_stream_ &&
+          (!check(hipEventRecord(lp_fork_, stream_), "hipEventRecord") || !check(hipStreamWaitEvent(fs, lp_fork_, 0), "hipStreamWaitEvent")))
+        return false;
+      if (!check(launch_remap_fused(lpa, fs), "fused remap launch")) return false;
+      lpa_launched = true;
+      snprintf(lpa_name, sizeof(lpa_name), "remap_fused_kernel<%d> + ", lpa.base.ks);
+      reset_lpa();
+      return true;
+    };
+    reset_lpa();
     const bool multi = n_frames > 1;
     for (int k = 0; k < njobs; k++) {
-      if (!lpf[(size_t)k] || lpa.base.nplanes >= 4) continue;
+      if (!lpf[(size_t)k]) continue;
+      if (lpa.base.nplanes == 4 && !flush_lpa()) return false;
       const PlaneJob& j = jobs[k];
       PlaneState& p = planes_[j.idx];
       const PlaneState::GatherPlan& gp = p.plan;
@@ -1241,17 +1260,8 @@ bool VideoFrameTransform::runPlanes(const PlaneJob* jobs, int njobs, int n_frame
       lpa.base.plane[lpa.base.nplanes++] = fp;
       lpa.base.total_tiles += fp.ntiles;
     }
-    if (lpa.base.nplanes > 0) {
-      finalize_launch(lpa.base);
-      hipStream_t fs = fuse_side_stream_ ? lp_streams_[2] : stream_;
-      if (fuse_side_stream_ &&
-          (!check(hipEventRecord(lp_fork_, stream_), "hipEventRecord") || !check(hipStreamWaitEvent(fs, lp_fork_, 0), "hipStreamWaitEvent")))
-        return false;
-      if (!check(launch_remap_fused(lpa, fs), "fused remap launch")) return false;
-      if (fuse_side_stream_ && !check(hipEventRecord(lp_join_[2], fs), "hipEventRecord")) return false;
-      lpa_launched = true;
-      snprintf(lpa_name, sizeof(lpa_name), "remap_fused_kernel<%d> + ", lpa.base.ks);
-    }
+    if (!flush_lpa()) return false;
+    if (lpa_launched && fuse_side_stream_ && !check(hipEventRecord(lp_join_[2], fs), "hipEventRecord")) return false;
   }
   // ---- stage 1: segmented low-pass into the scratch planes (filterPlane, :621-704) ----
   struct Src {
